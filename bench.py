@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training-throughput bench of the DeepLIO hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on):
 lidar-feat-pointseg (encoder, fusion=add, bypass simple, dropout .1) + imu-feat-rnn
@@ -45,6 +45,40 @@ def synth_batch(seed, B, S, C, H, W, T, device):
     q = torch.randn(B, S, 4, generator=g)
     f2g = torch.cat([torch.randn(B, S, 3, generator=g), q / q.norm(dim=-1, keepdim=True)], -1)
     return tuple(t.to(device) for t in (xyz, nrm, imu, f2f, f2g))
+
+
+DUMP_SAMPLE = 1 << 22       # elements kept of a larger dumped array: 16 MB of float32
+DUMP_SEED = 20261015
+
+
+def dump_sample(t, n=DUMP_SAMPLE):
+    """a 1-D float32 copy of t, or of n of its elements when it is larger: a fixed seeded sample (ascending indices that
+    depend only on t.numel()), so that two builds of the same workload are compared element for element"""
+    t = t.detach().reshape(-1)
+    if t.numel() > n:
+        g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+        idx = torch.randperm(t.numel(), generator=g)[:n].sort().values
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, ts, loss):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the parameters after its optimizer step, the
+    gradients it computed and the BatchNorm running statistics it updated -- as out_dir/<name>.npy (float32 / float64,
+    < 64 MB in all)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    stats = [b.detach().reshape(-1).float() for n, b in ts.model.named_buffers()
+             if b.is_floating_point() and n.rsplit(".", 1)[-1] in ("running_mean", "running_var")]
+    arrays = {
+        "loss": np.asarray([float(loss.item())], dtype=np.float64),
+        "params": dump_sample(ts.optimizer.flat),
+        "grads": dump_sample(ts.optimizer.grad),
+        "bn_running_stats": dump_sample(torch.cat(stats)) if stats else np.zeros(0, dtype=np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def usable_cores():
@@ -385,7 +419,12 @@ def main():
     ap.add_argument("--spawn", action="store_true", help="start the rank processes from here even for --gpus 1")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only: no model, works without a GPU (gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, parameters, gradients, "
+                         "BatchNorm running statistics; seeded samples of the larger ones) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
         sys.exit(self_launch(args.gpus, args.dry_run))
     if os.environ.get("DLIO_BENCH_WATCHDOG"):
@@ -579,6 +618,9 @@ def main():
         if not coop_fell_back() or attempt:
             break
     ops.prof_sample(1)
+    dumped = None
+    if args.dump_outputs and rank == 0:          # before anything else steps the model (host-fed region)
+        dumped = dump_outputs(args.dump_outputs, ts, loss)
     dt = sync.max_over_ranks(dt)
     exposed = sync.exposed_ms()
     dist_info = sync.describe() if world > 1 else None
@@ -766,6 +808,8 @@ def main():
                 # the n = 8 thread line beside the all-cores one (comparable with SURVEY's 8-core probe)
                 out["cpu_baseline"]["threads_8"] = cpu_baseline(cfg, C, H, W, T, S, args.cpu8_batch, args.cpu8_steps, threads=8)
             out["cpu_baseline"].update(cpu_parity_probe(cfg, C, H, W, T, S, args.cpu_batch, device))
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "names": dumped}
         print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()

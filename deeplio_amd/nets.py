@@ -439,7 +439,7 @@ class BaseLidarFeatNet(BaseNet):
         xyz, nrm = x[0], x[1]
         b, s, t, c, h, w = xyz.shape
         xa, xb = xyz.reshape(b * s, t * c, h, w), nrm.reshape(b * s, t * c, h, w)
-        if xyz.is_cuda and self.two_streams:
+        if xyz.is_cuda and self.two_streams and not torch.cuda.is_current_stream_capturing():   # (capture: one chain)
             # The two encoders are independent until the feature fusion: run the normals stream
             # on a second HIP stream so that its HBM-bound kernels (BN, pools) overlap the
             # MFMA-bound convolutions of the xyz stream and small layers fill idle CUs.
@@ -794,10 +794,11 @@ class DeepLIO(BaseNet):
             self._bn_counters += 1
         # The IMU branch (latency-bound persistent RNN kernels, 2 workgroups) is independent of the
         # lidar branch until the fusion layer: run it on a second HIP stream so it overlaps the
-        # convolutions; autograd replays each backward node on its forward stream.
+        # convolutions; autograd replays each backward node on its forward stream.  Under a hipGraph capture
+        # (tester.TestStep.capture) the branch stays on the capturing stream: the graph is one chain.
         side = None
         if (self.lidar_feat_net is not None and self.imu_feat_net is not None and torch.is_tensor(imu_meas)
-                and imu_meas.is_cuda and self.side_stream):
+                and imu_meas.is_cuda and self.side_stream and not torch.cuda.is_current_stream_capturing()):
             if self._side is None:
                 self._side = Fh.aux_stream(imu_meas.device, "imu")
             side = self._side

@@ -312,26 +312,35 @@ print("OK", done)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/deeplio"), reason="needs the reference checkout (build container)")
-def test_install_as_deeplio_overlays_the_real_reference(tmp_path):
-    """With the REAL reference on sys.path (third-party imports it lacks here stubbed as in
-    make_golden.install_stubs): after the install the reference's own `deeplio.models.trainer`
+STANDIN_TREE = dict(FAKE_TREE, **{    # ... plus the two modules of the reference's worker layer FAKE_TREE leaves out
+    "deeplio/common/spatial.py": "ORIGIN = 'reference spatial'\n",
+    "deeplio/models/tester.py": "from deeplio.common import spatial\nfrom deeplio.models import nets\n"
+                                "from .worker import Worker\n"
+                                "class Tester(Worker):\n"
+                                "    def se3_to_SE3(self, x, r):\n        raise RuntimeError('reference se3')\n",
+})
+
+
+def test_install_as_deeplio_overlays_a_standin_checkout(tmp_path):
+    """With a checkout of the reference's module layout on sys.path (the stand-in above: trainer,
+    worker, tester, datasets, common.spatial): after the install the checkout's own `deeplio.models.trainer`
     imports (train.py:13), its `nets` / `get_loss_function` / `create_optimizer` are this package, the
     model is constructed through the very call of trainer.py:52 (`nets.get_model(input_shape=..., cfg=...,
-    device=...)` after worker.py:41's `build_config_container`), `Trainer.se3_to_SE3` is the HIP chain,
-    and `deeplio.datasets` / `deeplio.common` / `deeplio.models.tester` are still the reference's."""
+    device=...)` after worker.py:41's `build_config_container`), `Trainer.se3_to_SE3` and `Tester.se3_to_SE3`
+    are the HIP chain, and `deeplio.datasets` / `deeplio.common` / `deeplio.models.tester` are still the checkout's."""
+    _write_tree(tmp_path, STANDIN_TREE)
     code = r"""
 import os, sys, types
-import make_golden as mg
-mg.install_stubs()
-sys.path.insert(0, mg.REF)
+REF = %r
+sys.path.insert(0, REF)
 import deeplio_amd
 done = deeplio_amd.install_as_deeplio()
 from deeplio.models.trainer import TrainerDeepLIO            # train.py:13, unmodified
 import deeplio.models.trainer as tr, deeplio.models.worker as wk, deeplio.models.tester as te
 import deeplio.datasets as ds, deeplio.common.spatial as sp
 for m in (tr, wk, te, ds, sp):
-    assert m.__file__.startswith(mg.REF), m.__file__
+    assert m.__file__.startswith(REF), m.__file__
+assert ds.Kitti.origin == 'reference dataset' and sp.ORIGIN == 'reference spatial'
 assert tr.nets is deeplio_amd.nets and tr.get_loss_function is deeplio_amd.losses.get_loss_function
 assert tr.create_optimizer is deeplio_amd.optimizer.create_optimizer
 assert tr.PolynomialLRDecay is deeplio_amd.misc.PolynomialLRDecay and tr.DataCombiCreater is deeplio_amd.misc.DataCombiCreater
@@ -350,8 +359,13 @@ try:
     raise SystemExit("the patched se3_to_SE3 should refuse CPU tensors")
 except RuntimeError as e:
     assert "no CPU fallback" in str(e), e
+try:
+    te.Tester.se3_to_SE3(types.SimpleNamespace(device='cpu'), torch.zeros(1, 2, 3), torch.zeros(1, 2, 3))
+    raise SystemExit("the patched Tester.se3_to_SE3 should refuse CPU tensors")
+except RuntimeError as e:
+    assert "no CPU fallback" in str(e), e
 print("OK", done)
-"""
+""" % str(tmp_path)
     r = _run_py(code, tmp_path)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
     assert "deeplio.models.trainer" in r.stdout and "deeplio.models.tester" in r.stdout

@@ -138,11 +138,23 @@ def test_bench_self_launch_two_ranks_share_the_gpu(dev):
     assert ds["allreduce_ms_exposed"] is not None and ds["allreduce_ms_exposed"] >= 0 and len(ds["buckets_bytes"]) in (1, 2)
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two HIP devices (RCCL refuses two ranks on one)")
 def test_bench_two_ranks_over_rccl(dev):
     """`python bench.py --gpus 2` on two devices: the default backend is nccl (= RCCL), anything else is refused; the
-    line proves the process group spanned two ranks"""
+    line proves the process group spanned two ranks.  On one device (RCCL refuses two ranks on one) both launch forms
+    must fail loudly instead of falling back: the self-launcher before it starts a rank, a torchrun-style rank without a
+    device of its own before it joins the rendezvous"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DLIO_DIST_BACKEND")}
+    if torch.cuda.device_count() < 2:
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=ROOT)
+        assert p.returncode != 0 and "1 HIP device(s) visible" in p.stderr, p.stderr[-2000:]
+        assert not [l for l in p.stdout.splitlines() if l.startswith("{")], p.stdout[-2000:]
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"],
+                           env=dict(env, WORLD_SIZE="2", RANK="1", LOCAL_RANK="1", MASTER_ADDR="127.0.0.1",
+                                    MASTER_PORT="29547"),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=ROOT)
+        assert p.returncode != 0 and "RCCL needs one device per rank" in p.stderr, p.stderr[-2000:]
+        return
     d = _run_env(env, "--gpus", "2", "--batch", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-isolated")
     ds = d["dist"]
     assert d["n_gpus"] == 2 and ds["backend"] == "nccl" and ds["world_size"] == 2 and ds["rank_sum"] == 3.0

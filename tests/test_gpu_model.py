@@ -277,19 +277,30 @@ def test_gradient_checksums_vs_reference_golden(dev, name):
     gradients' abs-sums with them and put both next to the fp64 oracle, so that the envelope of
     test_train_forward_backward_vs_oracle is evidence: HIP must be as close to the exact gradients as
     the reference's own arithmetic is (factor 3); the direct HIP-vs-reference difference is printed and
-    bounded by the two distances from fp64 (both are fp32 roundings of the same function)."""
+    bounded by the two distances from fp64 (both are fp32 roundings of the same function).  Where the reference's
+    backward fails (its in-place soft fusion; the golden then holds no `grad_sums`), the fp32 oracle -- the
+    same function out of place, torch fp32 arithmetic -- takes the reference's place, with the oracle envelope of
+    test_train_forward_backward_vs_oracle on the largest error."""
     gold = np.load(os.path.join(GOLD, "model_%s.npz" % name))
-    if not int(gold['has_bwd']):
-        pytest.skip("reference backward undefined for this configuration (SURVEY Q2)")
     _, model, crit, batch = build(name, dev, train=True)
     *_, loss = hip_step_forward(model, crit, batch)
     loss.backward()
     _, g64, _ = _oracle_grads(name, torch.float64)
     named = dict(model.named_parameters())
     named["criterion.sx"], named["criterion.sq"] = crit.sx, crit.sq
-    gsum = {k: v for k, v in zip(gold['grad_keys'].tolist(), gold['grad_sums'])}
-    assert set(gsum) == {k for k, p in named.items() if p.grad is not None}
-    scale = max(abs(v[1]) for v in gsum.values())
+    with_grad = {k for k, p in named.items() if p.grad is not None}
+    if int(gold['has_bwd']):
+        gsum = {k: float(v[1]) for k, v in zip(gold['grad_keys'].tolist(), gold['grad_sums'])}
+        assert set(gsum) == with_grad
+        max_floor, max_factor = 1e-3, 3.0
+    else:
+        _, g32, _ = _oracle_grads(name, torch.float32)
+        gsum = {k: float(v.abs().sum()) for k, v in g32.items()}
+        assert set(gsum) <= with_grad and set(gsum) == set(g64), sorted(set(gsum) ^ with_grad)
+        # the largest error is the envelope test_train_forward_backward_vs_oracle puts on the fp32 oracle's (its maximum over
+        # ~270 noise-dominated parameters is one sample of one rounding); median and per-parameter bounds as above
+        max_floor, max_factor = 2e-2, 10.0
+    scale = max(abs(v) for v in gsum.values())
     e_hip, e_ref, e_hip_ref = [], [], []
     for k, ref in gsum.items():
         exact = float(g64[k].abs().sum())
@@ -297,14 +308,14 @@ def test_gradient_checksums_vs_reference_golden(dev, name):
             continue
         mine = float(named[k].grad.detach().double().abs().sum())
         e_hip.append(abs(mine - exact) / exact)
-        e_ref.append(abs(float(ref[1]) - exact) / exact)
-        e_hip_ref.append(abs(mine - float(ref[1])) / abs(float(ref[1])))
+        e_ref.append(abs(ref - exact) / exact)
+        e_hip_ref.append(abs(mine - ref) / abs(ref))
     e_hip, e_ref, e_hip_ref = np.asarray(e_hip), np.asarray(e_ref), np.asarray(e_hip_ref)
     print("abs-sum of each parameter gradient, relative error: HIP vs fp64 median %.2e max %.2e | reference "
           "golden vs fp64 median %.2e max %.2e | HIP vs reference golden median %.2e max %.2e"
           % (np.median(e_hip), e_hip.max(), np.median(e_ref), e_ref.max(), np.median(e_hip_ref), e_hip_ref.max()))
     assert np.median(e_hip) <= max(1e-4, 3.0 * np.median(e_ref)), (np.median(e_hip), np.median(e_ref))
-    assert e_hip.max() <= max(1e-3, 3.0 * e_ref.max()), (e_hip.max(), e_ref.max())
+    assert e_hip.max() <= max(max_floor, max_factor * e_ref.max()), (e_hip.max(), e_ref.max())
     # HIP vs the reference's numbers directly: two fp32 roundings of the same function differ by up to the
     # sum of their distances from it, parameter by parameter
     sl = 3.0 * (e_hip + e_ref) + 1e-4

@@ -245,8 +245,8 @@ def test_teststep_matches_eval_model_and_tester_quaternions(dev):
 
 @pytest.mark.gpu
 def test_teststep_hipgraph_replay_is_bit_identical(dev):
-    """the captured test-mode forward (three streams inside one hipGraph) returns exactly what the
-    eager forward returns, also for new inputs copied into the static buffers"""
+    """the captured test-mode forward (one hipGraph, recorded on the capturing stream) returns exactly
+    what the eager three-stream forward returns, also for new inputs copied into the static buffers"""
     import sys
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import golden_common as gc
