@@ -165,10 +165,8 @@ SIGNATURES = {
     "dlio_lstm_layer_ok": (_i, [_i, _i, _i, _i, _i]),
     "dlio_lstm_layer_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "dlio_lstm_layer_fwd": (_i, [_p, _i] + [_p] * 8 + [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _sz, _p]),
-    "dlio_lstm_layer_wgrad": (_i, [_p, _p, _i, _p] + [_p] * 8 + [_i, _i, _i, _i, _i, _i, _p]),
     "dlio_lstm_layer_bwd": (_i, [_p, _i, _p, _i, _p, _p, _p] + [_p] * 4 + [_p] + [_p] * 8 + [_i, _p, _i, _i, _i, _i, _i, _i, _p,
                                  _sz, _p]),
-    "dlio_optim_set_max_blocks": (_i, [_i]),
     "dlio_soft_fusion_ok": (_i, [_i, _i, _i]),
     "dlio_soft_fusion_fwd": (_i, [_p, _i, _p, _i] + [_p] * 6 + [_i, _i, _i, _p]),
     "dlio_soft_fusion_bwd": (_i, [_p, _p, _i, _p, _i] + [_p] * 9 + [_i, _i, _i, _i, _p]),
@@ -216,10 +214,10 @@ SIGNATURES = {
     "dlio_gap_bf16_fwd": (_i, [_p, _i, _i, _p, _i, _i, _i, _p]),
     "dlio_gap_bf16_bwd": (_i, [_p, _p, _i, _i, _i, _p]),
     "dlio_cast_bf16": (_i, [_p, _p, _i64, _i, _p]),
-    "dlio_adam_step": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _f, _p]),
-    "dlio_sgd_step": (_i, [_p, _p, _p, _i64, _f, _f, _f, _i, _f, _p]),
-    "dlio_rmsprop_step": (_i, [_p, _p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _f, _p]),
-    "dlio_adadelta_step": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _p]),
+    "dlio_adam_step": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _f, _i, _p]),
+    "dlio_sgd_step": (_i, [_p, _p, _p, _i64, _f, _f, _f, _i, _f, _i, _p]),
+    "dlio_rmsprop_step": (_i, [_p, _p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _f, _i, _p]),
+    "dlio_adadelta_step": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _p]),
     "dlio_sumsq": (_i, [_p, _i64, _p, _p]),
 }
 

@@ -370,21 +370,6 @@ def _wgrad_stream(like):
     return aux_stream(like.device, "wgrad@%x" % ops.raw_stream())
 
 
-_PREP_SIDE = [os.environ.get("DLIO_PREP_SIDE", "0") != "0"]      # measured: median 18.63 ms with it, 18.38 without (ten alternations, round 6): off
-
-
-def _prep_side_stream(cur):
-    """where ops._PrepCache issues the long weight re-layout launches at the head of a step: the calling stream's weight-gradient
-    companion (idle until backward) -- the stems then queue behind the short three-piece launches only"""
-    if not (_PREP_SIDE[0] and _WGRAD_FORK[0]) or torch.cuda.is_current_stream_capturing():
-        return None
-    idx = cur.device.index if cur.device.index is not None else torch.cuda.current_device()
-    return _AUX.get((idx, "wgrad@%x" % cur.cuda_stream)) or aux_stream(cur.device, "wgrad@%x" % cur.cuda_stream)
-
-
-ops._PREP.side = _prep_side_stream
-
-
 def wgrad_stream_of(cur):
     """the weight-gradient companion of stream `cur`, if one exists (None: nothing was forked from it)"""
     idx = cur.device.index if cur.device.index is not None else torch.cuda.current_device()
@@ -1721,9 +1706,8 @@ class RNNFn(Function):
                     rw, rb = ow, ob
                 outs[wi], outs[with_bias_slot] = ow, ob
                 grads[wi], grads[with_bias_slot] = rw, rb
-                # sunk gradients accumulate from the first call on -- unless their slots are of the kind nobody zeroes
-                # (FlatOptimizer.set_overwritten): then this pass's first write replaces what is there
-                first[wi] = (not aw_) or bool(getattr(weights[wi], "_dlio_grad_overwrite", False))
+                # sunk gradients accumulate from the first call on
+                first[wi] = not aw_
 
         def acc_w(slot, dz, lddz, xin, ldx, N_, K, with_bias_slot):
             wi = slot
@@ -1883,10 +1867,6 @@ class HeadsFn(Function):
         return dx, sinks[0][2], sinks[1][2], sinks[2][2], sinks[3][2], None, None
 
 
-# the LSTM layer's weight-gradient launch forked onto the companion stream: the serial middle gets 60 us shorter and the step
-# 0.1 ms LONGER (median 18.07 against 17.96 ms, eight alternations: the launch then shares the hardware queue with the early
-# optimizer sweep and the first convolution weight gradients) -- off
-_LSTM_WGRAD_FORK = [os.environ.get("DLIO_LSTM_WGRAD_FORK", "0") != "0"]
 _LSTM_LAYER = [os.environ.get("DLIO_LSTM_LAYER", "1") != "0"]      # wide LSTMs: one launch sequence per LAYER (lstm_stream.hip)
 
 
@@ -1954,10 +1934,6 @@ class LstmStackFn(Function):
             if not acc and any(sk[1] for dd in sinks for sk in dd):     # one accumulate flag per launch: fresh buffers for all
                 sinks = [[_new(shapes[j], dout) for j in range(4)] for d in range(Dl)]
                 sinks = [[(t, False, t) for t in dd] for dd in sinks]
-            elif acc and all(getattr(weights[(l * D + d) * 4 + j], "_dlio_grad_overwrite", False)
-                             for d in range(Dl) for j in range(4)):
-                # FlatOptimizer.set_overwritten: these slots are not zeroed between steps, this launch is their one writer
-                acc = False
             for d in range(Dl):
                 for j in range(4):
                     grads[(l * D + d) * 4 + j] = sinks[d][j][2]
@@ -1967,17 +1943,8 @@ class LstmStackFn(Function):
                     grads[(l * D + d) * 4 + j] = None if a_ else t.zero_()
             wpairs = [(weights[(l * D + d) * 4], weights[(l * D + d) * 4 + 1]) for d in range(Dl)]
             outs = [tuple(sk[0] for sk in sinks[d]) for d in range(Dl)]
-            ws = _wgrad_stream(dout) if (acc and _LSTM_WGRAD_FORK[0]) else None
-            if ws is None:
-                ops.lstm_layer_bwd(dout, Dl * H, rec["inp"], Il, rec["hp"], rec["gates"], rec["cs"], wpairs, outs, acc, dinp, Il,
-                                   T, B, Il, H, Dl)
-            else:
-                # the weight-gradient launch (33 / 29 us on the step's serial chain) goes straight into the flat gradient buffer and
-                # nothing on the tape waits for it: forked onto the companion stream like the convolutions' weight gradients
-                dg = ops.lstm_layer_bwd(dout, Dl * H, rec["inp"], Il, rec["hp"], rec["gates"], rec["cs"], wpairs, None, acc, dinp,
-                                        Il, T, B, Il, H, Dl)
-                inp_l, hp_l = rec["inp"], rec["hp"]
-                _forked(ws, lambda: ops.lstm_layer_wgrad(dg, inp_l, Il, hp_l, outs, True, T, B, Il, H, Dl), dg, inp_l, hp_l)
+            ops.lstm_layer_bwd(dout, Dl * H, rec["inp"], Il, rec["hp"], rec["gates"], rec["cs"], wpairs, outs, acc, dinp, Il,
+                               T, B, Il, H, Dl)
             if l > 0:
                 prev = saved[l - 1]
                 dout = ops.dropout_bwd(dinp, prev["mask"], p) if "mask" in prev else dinp

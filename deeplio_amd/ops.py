@@ -121,7 +121,6 @@ class _PrepCache:
         self.tables = {}         # (device index, family) -> dict(items_dev, n, total, keys)
         self.waited = {}         # (stream handle, id of a refresh event) it has waited for (cleared by every refresh)
         self.batched = True
-        self.side = None         # callable(current stream) -> a stream for the long two-piece / bf16 family launches, or None
 
     @staticmethod
     def _floats(w, mode):
@@ -200,47 +199,36 @@ class _PrepCache:
         return t
 
     def _refresh_all(self, dev, cur):
-        """rebuild every registered layout (the optimizer changed the weights): the fp32-MFMA and three-piece families -- what
-        the stems and the first squeeze layers read -- on the calling stream; the two-piece / bf16 families (the long launches:
-        a magnitude pass + the split of every Fire and plain 3x3 weight, ~230 us at the headline shape) on `self.side(cur)`,
-        a stream that is idle at the head of a step (the caller's weight-gradient companion), so that the stems do not queue
-        behind them; every entry carries its family's event, a reader on another stream waits for it once"""
+        """rebuild every registered layout (the optimizer changed the weights) on the calling stream: first the fp32-MFMA and
+        three-piece families -- what the stems and the first squeeze layers read --, then the two-piece / bf16 families (the long
+        launches: a magnitude pass + the split of every Fire and plain 3x3 weight, ~230 us at the headline shape); every entry
+        carries its pair's event, a reader on another stream waits for it once (a stem layout's reader does not wait for the
+        long launches)"""
         for k in [k for k, e in self.entries.items() if e["ref"]() is None]:
             del self.entries[k]
             self.tables.pop((k[0], k[3] >> 1), None)
         self.waited.clear()
-        side = self.side(cur) if self.side is not None else None
-        groups = ((cur, ((0, lib.dlio_conv2d_prep_weights_batched, "conv2d_prep_weights_batched"),
-                         (1, lib.dlio_conv3x3_bx3_prep_batched, "conv3x3_bx3_prep_batched"))),
-                  (side if side is not None else cur,
-                   ((2, lib.dlio_conv_bf16_prep_batched, "conv_bf16_prep_batched"),
-                    (3, lib.dlio_conv_h2_prep_batched, "conv_h2_prep_batched"))))
-        for st, fams in groups:
+        groups = (((0, lib.dlio_conv2d_prep_weights_batched, "conv2d_prep_weights_batched"),
+                   (1, lib.dlio_conv3x3_bx3_prep_batched, "conv3x3_bx3_prep_batched")),
+                  ((2, lib.dlio_conv_bf16_prep_batched, "conv_bf16_prep_batched"),
+                   (3, lib.dlio_conv_h2_prep_batched, "conv_h2_prep_batched")))
+        for fams in groups:
             done = []
-            other = st is not cur and st.cuda_stream != cur.cuda_stream
-            if other:
-                st.wait_stream(cur)                        # the weights are final on the calling stream
-                prev = torch._C._cuda_getCurrentStream(st.device_index)
-                torch._C._cuda_setStream(stream_id=st.stream_id, device_index=st.device_index, device_type=st.device_type)
-            try:
-                for family, fn, name in fams:
-                    t = self._table(dev, family)
-                    if t is None:
-                        continue
-                    check(fn(_ptr(t["items"]), t["n"], t["total"], _stream()), name)
-                    done += t["keys"]
-            finally:
-                if other:
-                    torch._C._cuda_setStream(stream_id=prev[0], device_index=prev[1], device_type=prev[2])
+            for family, fn, name in fams:
+                t = self._table(dev, family)
+                if t is None:
+                    continue
+                check(fn(_ptr(t["items"]), t["n"], t["total"], _stream()), name)
+                done += t["keys"]
             if not done:
                 continue
             ev = torch.cuda.Event()
-            ev.record(st)
+            ev.record(cur)
             for k in done:
                 e = self.entries.get(k)
                 w = e["ref"]() if e is not None else None
                 if w is not None:
-                    e.update(epoch=self.epoch, version=w._version, stream=st.cuda_stream, event=ev)
+                    e.update(epoch=self.epoch, version=w._version, stream=cur.cuda_stream, event=ev)
 
 
 _PREP = _PrepCache()
@@ -1386,29 +1374,18 @@ def lstm_layer_fwd(x, ldx, w, hs, ldhs, T, B, I, H, D):
     return cs, hp, gates
 
 
-def lstm_layer_wgrad(dgates, x, ldx, hp, dws, accumulate, T, B, I, H, D):
-    """the layer's weight + bias gradients from lstm_layer_bwd(.., dws=None)'s dgates (one launch)"""
-    g1 = dws[1] if D == 2 else (None, None, None, None)
-    check(lib.dlio_lstm_layer_wgrad(_ptr(dgates), _ptr(x), ldx, _ptr(hp), _ptr(dws[0][0]), _ptr(dws[0][1]), _ptr(dws[0][2]),
-                                    _ptr(dws[0][3]), _ptr(g1[0]), _ptr(g1[1]), _ptr(g1[2]), _ptr(g1[3]), int(accumulate), T, B, I,
-                                    H, D, _stream()), "lstm_layer_wgrad")
-
-
 def lstm_layer_bwd(dhs, lddhs, x, ldx, hp, gates, cs, w, dws, accumulate, dx, lddx, T, B, I, H, D):
-    """w = per direction (w_ih, w_hh); dws = per direction (dw_ih, dw_hh, db_ih, db_hh) written (or accumulated into), or None:
-    the data path only (lstm_layer_wgrad takes the returned dgates); dx [rows][lddx] or None"""
+    """w = per direction (w_ih, w_hh); dws = per direction (dw_ih, dw_hh, db_ih, db_hh) written (or accumulated into);
+    dx [rows][lddx] or None"""
     rows = B * T
     dgates = torch.empty(D, rows, 4 * H, dtype=torch.float32, device=x.device)
     ws = workspace(lib.dlio_lstm_layer_ws_bytes(T, B, I, H, D), x.device, slot=2)
     w1 = w[1] if D == 2 else (None, None)
-    if dws is None:
-        dws = [(None, None, None, None)] * D
     g1 = dws[1] if D == 2 else (None, None, None, None)
     check(lib.dlio_lstm_layer_bwd(_ptr(dhs), lddhs, _ptr(x), ldx, _ptr(hp), _ptr(gates), _ptr(cs), _ptr(w[0][0]), _ptr(w[0][1]),
                                   _ptr(w1[0]), _ptr(w1[1]), _ptr(dgates), _ptr(dws[0][0]), _ptr(dws[0][1]), _ptr(dws[0][2]),
                                   _ptr(dws[0][3]), _ptr(g1[0]), _ptr(g1[1]), _ptr(g1[2]), _ptr(g1[3]), int(accumulate),
                                   _ptr(dx), lddx, T, B, I, H, D, _ptr(ws), ws.numel(), _stream()), "lstm_layer_bwd")
-    return dgates
 
 
 def gru_seq_fwd(gx, w_hh, b_hh, h0, hs, hs_off, ldhs, hp, gates, hT, T, B, H, rst, rsb, reverse):
@@ -1609,35 +1586,31 @@ def velo_image(proj_xyz, proj_remission, normals, proj_range, max_depth, channel
 
 
 # ----------------------------------------------------------------------------- optimizer
-def optim_set_max_blocks(blocks):
-    """workgroups the optimizer sweeps may use (0: default)"""
-    check(lib.dlio_optim_set_max_blocks(int(blocks)), "optim_set_max_blocks")
-
-
-def adam_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, max_blocks=0):
+    """max_blocks > 0 caps the sweep's grid (the optimizer sweeps below likewise; 0: the default grid)"""
     weights_changed()
     check(lib.dlio_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(beta1),
-                             float(beta2), float(eps), float(wd), int(step), float(grad_scale),
+                             float(beta2), float(eps), float(wd), int(step), float(grad_scale), int(max_blocks),
                              _stream()), "adam_step")
 
 
-def sgd_step(p, g, buf, lr, momentum, wd, step, grad_scale=1.0):
+def sgd_step(p, g, buf, lr, momentum, wd, step, grad_scale=1.0, max_blocks=0):
     weights_changed()
     check(lib.dlio_sgd_step(_ptr(p), _ptr(g), _ptr(buf), p.numel(), float(lr), float(momentum),
-                            float(wd), int(step), float(grad_scale), _stream()), "sgd_step")
+                            float(wd), int(step), float(grad_scale), int(max_blocks), _stream()), "sgd_step")
 
 
-def rmsprop_step(p, g, square_avg, buf, grad_avg, lr, alpha, eps, wd, momentum, grad_scale=1.0):
+def rmsprop_step(p, g, square_avg, buf, grad_avg, lr, alpha, eps, wd, momentum, grad_scale=1.0, max_blocks=0):
     weights_changed()
     check(lib.dlio_rmsprop_step(_ptr(p), _ptr(g), _ptr(square_avg), _ptr(buf), _ptr(grad_avg), p.numel(),
                                 float(lr), float(alpha), float(eps), float(wd), float(momentum),
-                                float(grad_scale), _stream()), "rmsprop_step")
+                                float(grad_scale), int(max_blocks), _stream()), "rmsprop_step")
 
 
-def adadelta_step(p, g, square_avg, acc_delta, lr, rho, eps, wd, grad_scale=1.0):
+def adadelta_step(p, g, square_avg, acc_delta, lr, rho, eps, wd, grad_scale=1.0, max_blocks=0):
     weights_changed()
     check(lib.dlio_adadelta_step(_ptr(p), _ptr(g), _ptr(square_avg), _ptr(acc_delta), p.numel(), float(lr),
-                                 float(rho), float(eps), float(wd), float(grad_scale), _stream()),
+                                 float(rho), float(eps), float(wd), float(grad_scale), int(max_blocks), _stream()),
           "adadelta_step")
 
 

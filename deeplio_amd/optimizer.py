@@ -20,6 +20,12 @@ def _join():
 
 
 class FlatOptimizer:
+    """The flat-buffer base of the optimizers below.  step() updates every element.  One step may be split in two: step_early(lo)
+    updates [lo:] before step() (from inside backward, as soon as those gradients are final), and the step() that follows updates
+    [:lo] only.  The contract: at most one step_early() per step(), its caller orders `stream` behind the kernels that wrote the
+    gradients [lo:], and nothing changes those gradients between the two calls (one backward pass: TrainStep.step arms the
+    early sweep for its own pass only)."""
+
     def __init__(self, params, lr, weight_decay):
         groups = list(params)
         if groups and not isinstance(groups[0], dict):
@@ -60,8 +66,9 @@ class FlatOptimizer:
         self._early = None           # (lo, event): [lo:] of this step was already updated by step_early()
         self.early_blocks = int(os.environ.get("DLIO_EARLY_STEP_BLOCKS", "256"))
 
-    def _apply(self, lo, hi, count):
-        """the update rule over elements [lo:hi) of the flat buffers (one launch); `count` = this step's number"""
+    def _apply(self, lo, hi, count, max_blocks=0):
+        """the update rule over elements [lo:hi) of the flat buffers (one launch); `count` = this step's number; max_blocks > 0
+        caps the launch's grid"""
         raise NotImplementedError
 
     @torch.no_grad()
@@ -81,9 +88,9 @@ class FlatOptimizer:
     def step_early(self, lo, stream=None):
         """update elements [lo:] NOW -- their gradients are final although backward is still running (TrainStep: everything
         behind the feature nets, 87 % of the headline model, is final when backward reaches the fusion output) -- on `stream`
-        (which must already be ordered behind the kernels that wrote those gradients); the following step() then only
-        updates [:lo] and waits for this launch.  The end of the step loses the 165 MB x 7 sweep's largest part: it runs
-        under the encoder backward instead of behind it."""
+        (the caller orders it behind the kernels that wrote those gradients); the following step() then only updates [:lo]
+        and waits for this launch.  The end of the step loses the 165 MB x 7 sweep's largest part: it runs under the encoder
+        backward instead of behind it.  Once per step(): a second call before step() does nothing and returns False."""
         lo = int(lo)
         if self._early is not None or lo <= 0 or lo >= self.flat.numel() or lo % 4:
             return False
@@ -92,56 +99,30 @@ class FlatOptimizer:
         #  Linear / RNN parameters only -- no convolution layouts -- and a bump now would make any on-demand layout fetch of
         #  the backward pass still running rebuild every layout)
         epoch = ops._PREP.epoch
-        # background work: a small grid (one workgroup per CU) leaves the chip to the critical chain it runs beside
-        ops.optim_set_max_blocks(self.early_blocks)
-        if stream is None:
-            self._apply(lo, self.flat.numel(), self.step_count + 1)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-        else:
-            from .functional import on_stream
-            with on_stream(stream):
-                self._apply(lo, self.flat.numel(), self.step_count + 1)
+        try:
+            # background work: a small grid (one workgroup per CU) leaves the chip to the critical chain it runs beside
+            if stream is None:
+                self._apply(lo, self.flat.numel(), self.step_count + 1, self.early_blocks)
                 ev = torch.cuda.Event()
-                ev.record(stream)
-        ops.optim_set_max_blocks(0)
-        ops._PREP.epoch = epoch
+                ev.record(torch.cuda.current_stream())
+            else:
+                from .functional import on_stream
+                with on_stream(stream):
+                    self._apply(lo, self.flat.numel(), self.step_count + 1, self.early_blocks)
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+        finally:
+            ops._PREP.epoch = epoch
         self._early = (lo, ev)
         return True
 
-    def set_overwritten(self, params):
-        """`params` (a contiguous run of this optimizer's parameters, in order): their gradient slots are OVERWRITTEN by their
-        producer in every backward pass (functional.LstmStackFn writes a layer's weight gradients in one launch, exactly once)
-        or never written at all (a direction that is not run: stays zero) -- zero_grad() then skips them: no fill over, and no
-        read-modify-write into, the 143 MB of the odometry LSTM's gradients.  Only for a loop that runs exactly one backward
-        pass per step (TrainStep): gradient accumulation over several passes needs the default.  None / empty: off."""
-        self._skip = None
-        for p in self.params:
-            if hasattr(p, "_dlio_grad_overwrite"):
-                del p._dlio_grad_overwrite
-        ps = list(params or [])
-        if not ps:
-            return
-        index = {id(p): i for i, p in enumerate(self.params)}
-        idx = sorted(index[id(p)] for p in ps)
-        if idx != list(range(idx[0], idx[0] + len(idx))):
-            raise ValueError("set_overwritten needs a contiguous run of parameters")
-        lo = self.offsets[idx[0]]
-        hi = self.offsets[idx[-1] + 1] if idx[-1] + 1 < len(self.offsets) else self.flat.numel()
-        self.grad[lo:hi].zero_()                 # (the slots nobody ever writes must hold zeros from now on)
-        for p in ps:
-            p._dlio_grad_overwrite = True
-        self._skip = (lo, hi)
+    def discard_early(self):
+        """forget a step_early() whose step() never came (the pass raised in between): that sweep stands -- the caller restores
+        its last good state after an error --, but the next step() updates the whole buffer"""
+        self._early = None
 
     def zero_grad(self, set_to_none=False):
-        skip = getattr(self, "_skip", None)
-        if skip is None:
-            self.grad.zero_()
-        else:
-            if skip[0] > 0:
-                self.grad[:skip[0]].zero_()
-            if skip[1] < self.grad.numel():
-                self.grad[skip[1]:].zero_()
+        self.grad.zero_()
         for p, o in zip(self.params, self.offsets):   # keep .grad views attached
             if p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + 4 * o:
                 p.grad = self.grad[o:o + p.numel()].view(p.shape)
@@ -192,10 +173,10 @@ class Adam(FlatOptimizer):
     def _state(self):
         return {'exp_avg': self.exp_avg, 'exp_avg_sq': self.exp_avg_sq}
 
-    def _apply(self, lo, hi, count):
+    def _apply(self, lo, hi, count, max_blocks=0):
         lr, wd = self._hyper()
         ops.adam_step(self.flat[lo:hi], self.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], lr, self.betas[0],
-                      self.betas[1], self.eps, wd, count, self.grad_scale)
+                      self.betas[1], self.eps, wd, count, self.grad_scale, max_blocks)
 
 
 class SGD(FlatOptimizer):
@@ -207,9 +188,10 @@ class SGD(FlatOptimizer):
     def _state(self):
         return {'momentum_buffer': self.buf}
 
-    def _apply(self, lo, hi, count):
+    def _apply(self, lo, hi, count, max_blocks=0):
         lr, wd = self._hyper()
-        ops.sgd_step(self.flat[lo:hi], self.grad[lo:hi], self.buf[lo:hi], lr, self.momentum, wd, count, self.grad_scale)
+        ops.sgd_step(self.flat[lo:hi], self.grad[lo:hi], self.buf[lo:hi], lr, self.momentum, wd, count, self.grad_scale,
+                     max_blocks)
 
 
 class RMSprop(FlatOptimizer):
@@ -230,11 +212,11 @@ class RMSprop(FlatOptimizer):
             st['grad_avg'] = self.grad_avg
         return st
 
-    def _apply(self, lo, hi, count):
+    def _apply(self, lo, hi, count, max_blocks=0):
         lr, wd = self._hyper()
         ops.rmsprop_step(self.flat[lo:hi], self.grad[lo:hi], self.square_avg[lo:hi],
                          None if self.buf is None else self.buf[lo:hi], None if self.grad_avg is None else self.grad_avg[lo:hi],
-                         lr, self.alpha, self.eps, wd, self.momentum, self.grad_scale)
+                         lr, self.alpha, self.eps, wd, self.momentum, self.grad_scale, max_blocks)
 
 
 class Adadelta(FlatOptimizer):
@@ -249,10 +231,10 @@ class Adadelta(FlatOptimizer):
     def _state(self):
         return {'square_avg': self.square_avg, 'acc_delta': self.acc_delta}
 
-    def _apply(self, lo, hi, count):
+    def _apply(self, lo, hi, count, max_blocks=0):
         lr, wd = self._hyper()
         ops.adadelta_step(self.flat[lo:hi], self.grad[lo:hi], self.square_avg[lo:hi], self.acc_delta[lo:hi], lr, self.rho,
-                          self.eps, wd, self.grad_scale)
+                          self.eps, wd, self.grad_scale, max_blocks)
 
 
 def create_optimizer(params, cfg, args, **kwargs):

@@ -60,19 +60,10 @@ class TrainStep:
         self._poll_host = None
         # the optimizer step over the tail bucket issued from inside backward (see _tail_ready); 0: one sweep at the end
         self.early_tail_step = os.environ.get("DLIO_EARLY_TAIL_STEP", "1") != "0"
-        # (the gradient buffer's fill beside the forward pass instead of in the serial middle: median 18.00 against 17.96 ms,
-        #  eight alternations -- no gain: off)
-        self.zero_grad_early = os.environ.get("DLIO_ZERO_GRAD_EARLY", "0") != "0"
+        self._armed = False                         # inside step()'s forward + backward: _tail_ready acts
         self._tail_lo = self.tail_offset()
         if self._tail_lo is not None and (self._tail_lo <= 0 or self._tail_lo % 4):
             self._tail_lo = None
-        self.model.tail_grads_ready = self._tail_ready
-        # DLIO_GRAD_OVERWRITE=1: the odometry LSTM's gradient slots (143 of the 165 MB) are written once per step by
-        # functional.LstmStackFn and neither zero-filled nor read back (FlatOptimizer.set_overwritten).  Bit-identical training
-        # (test_lstm_gradient_slots_overwritten_instead_of_zeroed), 190 MB less traffic per step -- and no measurable gain
-        # (median 18.35 against 18.38 ms, ten alternations): off by default, the plain fill + accumulate contract stays
-        self.overwrite_lstm_grads = os.environ.get("DLIO_GRAD_OVERWRITE", "0") != "0"
-        self._set_overwritten()
         self.model.train()
         if grad_sync is not None:
             self.set_grad_sync(grad_sync)
@@ -88,31 +79,19 @@ class TrainStep:
         index = {id(p): i for i, p in enumerate(self.optimizer.params)}
         return self.optimizer.offsets[index[id(first)]]
 
-    def _set_overwritten(self):
-        from .nets import OdomFeatRNN
-        net = self.model.odom_feat_net
-        ok = (self.overwrite_lstm_grads and isinstance(net, OdomFeatRNN) and hasattr(self.optimizer, "set_overwritten")
-              and self.device.type == "cuda" and net.rnn.mode == "lstm" and Fh._LSTM_LAYER[0])
-        if ok:
-            r = net.rnn
-            D = 2 if r.bidirectional else 1
-            B = self.args.batch_size
-            S = self.model.seq_size
-            ok = (B <= 8 and all(ops.lstm_layer_ok(S, B, r.input_size if l == 0 else D * r.hidden_size, r.hidden_size, D)
-                                 for l in range(r.num_layers))
-                  and all(p.requires_grad for p in r.parameters()))
-        self.optimizer.set_overwritten(list(net.rnn.parameters()) if ok else None)
-
     def _tail_ready(self):
         """autograd hook on the fusion output's gradient: everything behind the feature nets (odometry net, heads, loss weights:
         [tail_offset():] of the flat buffers, 87 % of the headline model) has its final gradient.  Data parallel: start that
         bucket's all-reduce; then run the optimizer over it NOW on the 'comm' stream (beside a weight-gradient companion,
-        functional.assign_streams) -- under the encoder backward instead of at the end of the step."""
+        functional.assign_streams) -- under the encoder backward instead of at the end of the step.  Only while step() runs its
+        own pass: a backward pass elsewhere (gradient inspection, accumulation over several passes) leaves the weights alone."""
+        if not self._armed:
+            return
         sync = self.grad_sync
         dp = sync is not None and sync.world > 1
         if dp and sync.tail_lo is not None:
             sync.reduce_tail_async()
-        if not self.early_tail_step or self._tail_lo is None or not hasattr(self.optimizer, "step_early"):
+        if not self.early_tail_step or self._tail_lo is None:
             return
         if dp and not isinstance(getattr(sync, "_tail_work", None), torch.cuda.Event):
             return                     # (the bucket is not being reduced on the comm stream: the whole step at the end)
@@ -177,7 +156,7 @@ class TrainStep:
 
     def _tail(self, feats, gts_f2f, gts_f2g, hook=True):
         """features -> loss: the model's last layers, NaN/Inf flags, SE(3) chain, criterion"""
-        pred_f2f_t, pred_f2f_w = self.model.forward_tail(feats, grads_ready_hook=hook)
+        pred_f2f_t, pred_f2f_w = self.model.forward_tail(feats, on_tail_grads=self._tail_ready if hook else None)
         crit, lt = self.criterion, self.criterion.loss_Types
         g0, g1 = 1, min(self.max_glob_seq + 1, pred_f2f_t.shape[1])
         if (self.fused_tail and pred_f2f_t.is_cuda and g0 < g1 and (lt[0] or lt[1]) and hasattr(crit, "mode")
@@ -206,31 +185,18 @@ class TrainStep:
         self._steps += 1
         self._manage_gc()
         Fh.lazy_clear()            # (entries a failed backward pass may have left behind)
-        if getattr(self.optimizer, "_early", None) is not None:
-            # a pass that raised between its early tail sweep and optimizer.step(): that sweep stands (the caller restores its
-            # last good state after an error), its marker must not make THIS step skip the tail
-            self.optimizer._early = None
-        zero_ev = None
-        if self.zero_grad_early and self.device.type == "cuda" and getattr(self.model, "side_stream", True):
-            # the 165 MB fill of the flat gradient buffer runs on the `comm` stream beside the forward pass (its hardware queue is
-            # idle until backward) instead of between the loss and backward(), in the step's serial middle
-            comm = Fh.aux_stream(self.device, "comm")
-            cur = Fh.current_stream_obj()
-            comm.wait_stream(cur)                  # behind the previous step's optimizer sweep
-            with Fh.on_stream(comm):
-                self.optimizer.zero_grad()
-                zero_ev = torch.cuda.Event()
-                zero_ev.record(comm)
-        loss = self._tail(self.model.forward_features([[imgs, normals], imus]), gts_f2f, gts_f2g)
-        if zero_ev is None:
+        self.optimizer.discard_early()         # (the marker of a pass that raised before its optimizer.step())
+        self._armed = True
+        try:
+            loss = self._tail(self.model.forward_features([[imgs, normals], imus]), gts_f2f, gts_f2g)
             self.optimizer.zero_grad()
-        else:
-            Fh.current_stream_obj().wait_event(zero_ev)
-        if self.autograd_inline:
-            with torch.autograd.set_multithreading_enabled(False):
-                loss.backward(self._one)           # (an explicit d loss / d loss: no fill launch per step)
-        else:
-            loss.backward(self._one)
+            if self.autograd_inline:
+                with torch.autograd.set_multithreading_enabled(False):
+                    loss.backward(self._one)       # (an explicit d loss / d loss: no fill launch per step)
+            else:
+                loss.backward(self._one)
+        finally:
+            self._armed = False
         if self.grad_sync is not None:
             self.grad_sync.all_reduce_grads()
         self.optimizer.step()

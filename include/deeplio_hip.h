@@ -42,7 +42,7 @@ typedef void* dlio_stream_t;
  * at build time (deeplio_amd/build.py passes it in).  The ctypes binding (deeplio_amd/_lib.py)
  * compares both against the header next to it when it loads the library, so a stale .so fails at
  * import instead of being called with a changed signature. */
-#define DLIO_ABI_VERSION 243
+#define DLIO_ABI_VERSION 244
 int dlio_version(void);
 uint32_t dlio_abi_hash(void);
 const char* dlio_arch(void);
@@ -525,12 +525,6 @@ int dlio_lstm_layer_fwd(const float* x, int ldx, const float* w_ih0, const float
                         const float* w_hh1, const float* b_ih1, const float* b_hh1, float* hs,
                         int ldhs, float* cs, float* hp, float* gates, int T, int B, int I, int H,
                         int D, void* ws, size_t ws_bytes, dlio_stream_t stream);
-/* the weight-gradient launch of dlio_lstm_layer_bwd on its own (dlio_lstm_layer_bwd with dw_ih0 == NULL skips it): nothing
- * downstream on the tape reads these gradients, the caller may issue it on a companion stream behind the data path */
-int dlio_lstm_layer_wgrad(const float* dgates, const float* x, int ldx, const float* hp, float* dw_ih0,
-                          float* dw_hh0, float* db_ih0, float* db_hh0, float* dw_ih1, float* dw_hh1,
-                          float* db_ih1, float* db_hh1, int accumulate, int T, int B, int I, int H,
-                          int D, dlio_stream_t stream);
 int dlio_lstm_layer_bwd(const float* dhs, int lddhs, const float* x, int ldx, const float* hp,
                         const float* gates, const float* cs, const float* w_ih0,
                         const float* w_hh0, const float* w_ih1, const float* w_hh1, float* dgates,
@@ -896,27 +890,28 @@ int dlio_cast_bf16(const void* src, void* dst, int64_t n, int dir, dlio_stream_t
  * torch.optim.Adam / SGD(momentum) / RMSprop / Adadelta as built by create_optimizer
  * (optimizer.py:4-16) over ONE flat parameter buffer: weight decay is L2 added
  * to the gradient.  step is the 1-based step count. grad_scale multiplies g
- * first (data-parallel averaging). */
-/* workgroups the sweeps below may use (0 = default, 8 per CU): a sweep issued under the backward pass (the tail bucket's early
- * update, FlatOptimizer.step_early) runs as background work on a small grid */
-int dlio_optim_set_max_blocks(int blocks);
+ * first (data-parallel averaging).  max_blocks > 0 caps the grid (0 = default, 8
+ * workgroups per CU): a sweep issued under the backward pass (the tail bucket's early update,
+ * FlatOptimizer.step_early) runs as background work on a small grid. */
 int dlio_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step,
-                   float grad_scale, dlio_stream_t stream);
+                   float grad_scale, int max_blocks, dlio_stream_t stream);
 int dlio_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
-                  float weight_decay, int step, float grad_scale, dlio_stream_t stream);
+                  float weight_decay, int step, float grad_scale, int max_blocks,
+                  dlio_stream_t stream);
 /* torch.optim.RMSprop (optimizer.py:12-13): square_avg = alpha*square_avg + (1-alpha) g^2;
  * centered (grad_avg != NULL): avg = sqrt(square_avg - grad_avg^2) + eps; momentum != 0
  * (momentum_buf != NULL): buf = momentum*buf + g/avg, p -= lr*buf; else p -= lr*g/avg. */
 int dlio_rmsprop_step(float* p, const float* g, float* square_avg, float* momentum_buf,
                       float* grad_avg, int64_t n, float lr, float alpha, float eps,
-                      float weight_decay, float momentum, float grad_scale, dlio_stream_t stream);
+                      float weight_decay, float momentum, float grad_scale, int max_blocks,
+                      dlio_stream_t stream);
 /* torch.optim.Adadelta (optimizer.py:14-15): square_avg = rho*square_avg + (1-rho) g^2;
  * delta = sqrt(acc_delta+eps)/sqrt(square_avg+eps) * g; acc_delta = rho*acc_delta + (1-rho) delta^2;
  * p -= lr*delta. */
 int dlio_adadelta_step(float* p, const float* g, float* square_avg, float* acc_delta, int64_t n,
                        float lr, float rho, float eps, float weight_decay, float grad_scale,
-                       dlio_stream_t stream);
+                       int max_blocks, dlio_stream_t stream);
 /* out[0] = sum g^2 (fp64) -- calc_grad_norm, trainer.py:481-486 */
 int dlio_sumsq(const float* g, int64_t n, double* out, dlio_stream_t stream);
 

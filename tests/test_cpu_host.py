@@ -50,7 +50,7 @@ def test_cooperative_batchnorm_mode_switch_needs_no_device():
     assert lib.dlio_bn_coop_get_mode() == default
 
 
-def test_error_codes_map_to_reference_style_exceptions():
+def test_error_codes_map_to_reference_style_exceptions_and_arguments_are_checked_first():
     from deeplio_amd import _lib
     with pytest.raises(ValueError):
         _lib.check(_lib.DLIO_EINVAL, "x")
@@ -59,8 +59,15 @@ def test_error_codes_map_to_reference_style_exceptions():
     with pytest.raises(RuntimeError):
         _lib.check(_lib.DLIO_EWS, "x")
     # argument validation happens before any launch: no GPU needed
-    assert _lib.lib.dlio_conv2d_fwd(None, None, None, None, None, None, None, None, None, None) == _lib.DLIO_EINVAL
-    assert _lib.lib.dlio_adam_step(None, None, None, None, 0, 0., 0., 0., 0., 0., 1, 1., None) == _lib.DLIO_EINVAL
+    lib = _lib.lib
+    assert lib.dlio_conv2d_fwd(None, None, None, None, None, None, None, None, None, None) == _lib.DLIO_EINVAL
+    assert lib.dlio_adam_step(None, None, None, None, 0, 0., 0., 0., 0., 0., 1, 1., 0, None) == _lib.DLIO_EINVAL
+    # a negative grid cap is refused before the pointers are used (these are never dereferenced)
+    p = 256
+    assert lib.dlio_adam_step(p, p, p, p, 4, 1e-3, .9, .999, 1e-8, 0., 1, 1., -1, None) == _lib.DLIO_EINVAL
+    assert lib.dlio_sgd_step(p, p, p, 4, 1e-3, .9, 0., 1, 1., -1, None) == _lib.DLIO_EINVAL
+    assert lib.dlio_rmsprop_step(p, p, p, None, None, 4, 1e-2, .99, 1e-8, 0., 0., 1., -1, None) == _lib.DLIO_EINVAL
+    assert lib.dlio_adadelta_step(p, p, p, p, 4, 1., .9, 1e-6, 0., 1., -1, None) == _lib.DLIO_EINVAL
 
 
 def test_product_never_imports_the_oracle():

@@ -1257,31 +1257,20 @@ def test_cooperative_batchnorm_modes_train_bit_identically(dev):
             assert torch.equal(other[2][k], res[0][2][k]), k
 
 
-def test_lstm_gradient_slots_overwritten_instead_of_zeroed(dev):
-    """TrainStep marks the odometry LSTM's gradient slots as overwritten by their producer (FlatOptimizer.set_overwritten:
-    functional.LstmStackFn writes a layer's weight gradients in one launch, exactly once per backward pass; the discarded
-    direction's slots are never written and stay zero): zero_grad() skips them, the weight-gradient launch does not read them
-    back.  Parameters and Adam moments after three steps are BIT-identical to the zero-fill + accumulate path, also when a
-    step falls back to the per-direction RNNFn (a batch the layer kernels do not take) -- its first write then replaces the
-    stale contents (optimizer.py:4-16, trainer.py:263-266).  Off by default (DLIO_GRAD_OVERWRITE: no measurable gain)."""
+def test_lstm_layer_fallback_step_trains_fp32_close(dev):
+    """A step that falls back to the per-direction RNNFn (a batch the layer kernels do not take) in the middle of
+    functional.LstmStackFn steps computes the same gradients through other kernels, into the same accumulate-into-.grad
+    slots: three steps train to fp32-close losses (optimizer.py:4-16, trainer.py:263-266)."""
     from deeplio_amd import functional as Fh
     from deeplio_amd.config import make_config
     from deeplio_amd.trainer import TrainStep
     g = dict(B=2, S=2, C=5, H=16, W=64, T=7)
     batch = tuple(t.to(dev) for t in gc.make_batch(2000, g['B'], g['S'], g['C'], g['H'], g['W'], g['T']))
     res = []
-    for over, fallback_step in ((True, None), (False, None), (True, 1), (False, 1)):
+    for fallback_step in (None, 1):
         cfg = make_config(seq=2, overrides=dict(gc.NO_DROP, **{'odom-feat-rnn/hidden-size': 256}))
-        os.environ["DLIO_GRAD_OVERWRITE"] = "1" if over else "0"
-        try:
-            ts = TrainStep(cfg, (g['C'], g['H'], g['W']), dev, g['B'])
-        finally:
-            os.environ.pop("DLIO_GRAD_OVERWRITE", None)
+        ts = TrainStep(cfg, (g['C'], g['H'], g['W']), dev, g['B'])
         gc.fill_state(ts.model, seed=1000)
-        skip = getattr(ts.optimizer, "_skip", None)
-        assert (skip is not None) == over
-        if over:
-            assert skip[1] - skip[0] == sum((p.numel() + 15) // 16 * 16 for p in ts.model.odom_feat_net.rnn.parameters())
         losses = []
         for i in range(3):
             Fh._LSTM_LAYER[0] = i != fallback_step
@@ -1291,10 +1280,110 @@ def test_lstm_gradient_slots_overwritten_instead_of_zeroed(dev):
                 Fh._LSTM_LAYER[0] = True
         ts.check()
         torch.cuda.synchronize()
-        res.append((losses, ts.optimizer.flat.clone(), ts.optimizer.exp_avg.clone(), ts.optimizer.exp_avg_sq.clone()))
+        res.append(losses)
         ts.release_gc()
-    for (la, pa, ma, va), (lb, pb, mb, vb) in ((res[0], res[1]), (res[2], res[3])):
-        assert la == lb and torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb)
-    # (the fallback step computes the same gradients through other kernels: fp32-close losses; Adam's sign-like first updates
-    #  turn that into parameter differences of a few 1e-4)
-    assert abs(res[2][0][2] - res[0][0][2]) <= 1e-3 * abs(res[0][0][2])
+    # (Adam's sign-like first updates turn the fallback's rounding differences into parameter differences of a few 1e-4)
+    assert abs(res[1][2] - res[0][2]) <= 1e-3 * abs(res[0][2])
+
+
+def _headline_step(dev, optim="adam"):
+    from deeplio_amd import functional as Fh
+    from deeplio_amd.trainer import TrainStep
+    name = "pointseg_lstm_cat"
+    g = gc.MODEL_CASES[name]['geom']
+    cfg = gc.case_cfg(name)
+    cfg['optimizer'] = optim
+    Fh.manual_seed(11)
+    ts = TrainStep(cfg, (g['C'], g['H'], g['W']), dev, g['B'])
+    gc.fill_state(ts.model, seed=1000)
+    batches = [tuple(t.to(dev) for t in gc.make_batch(seed, g['B'], g['S'], g['C'], g['H'], g['W'], g['T']))
+               for seed in (2000, 2001)]
+    return ts, batches
+
+
+def _manual_backward(ts, b):
+    loss = ts._tail(ts.model.forward_features([[b[0], b[1]], b[2]]), b[3], b[4])
+    loss.backward()
+
+
+def test_backward_outside_step_leaves_the_weights_alone(dev):
+    """The early optimizer sweep (FlatOptimizer.step_early from TrainStep._tail_ready) is armed by TrainStep.step only: a
+    training-mode forward + backward through the same model outside step() leaves parameters and optimizer state bit-unchanged
+    and no early-sweep marker behind, and the next step() still takes the early sweep exactly once."""
+    ts, (batch, _) = _headline_step(dev)
+    try:
+        opt = ts.optimizer
+        assert ts.early_tail_step and ts._tail_lo is not None
+        calls = []
+        step_early = opt.step_early
+
+        def counting(lo, stream=None):
+            calls.append(lo)
+            return step_early(lo, stream)
+        opt.step_early = counting
+        flat0 = opt.flat.clone()
+        st0 = {k: v.clone() for k, v in opt._state().items()}
+        opt.zero_grad()
+        _manual_backward(ts, batch)
+        torch.cuda.synchronize()
+        assert calls == [] and opt._early is None and opt.step_count == 0
+        assert float(opt.grad[ts._tail_lo:].abs().max()) > 0          # (the tail's gradients did arrive)
+        assert torch.equal(opt.flat, flat0)
+        for k, v in opt._state().items():
+            assert torch.equal(v, st0[k]), k
+        ts.step(*batch)
+        ts.check()
+        torch.cuda.synchronize()
+        assert calls == [ts._tail_lo] and opt.step_count == 1 and opt._early is None
+        assert not torch.equal(opt.flat[ts._tail_lo:], flat0[ts._tail_lo:])
+    finally:
+        ts.release_gc()
+
+
+def test_gradient_accumulation_is_independent_of_the_early_sweep(dev):
+    """Two backward passes into the same gradient buffer, then one optimizer.step() (gradient accumulation outside
+    TrainStep.step): parameters and Adam moments are bit-identical whether TrainStep's early tail sweep is on or off -- the
+    whole buffer is updated once, from the sum of both passes."""
+    res = []
+    for early in (True, False):
+        ts, batches = _headline_step(dev)
+        try:
+            ts.early_tail_step = early
+            opt = ts.optimizer
+            opt.zero_grad()
+            for b in batches:
+                _manual_backward(ts, b)
+            opt.step()
+            torch.cuda.synchronize()
+            assert opt.step_count == 1 and opt._early is None
+            res.append((opt.grad.clone(), opt.flat.clone(), {k: v.clone() for k, v in opt._state().items()}))
+        finally:
+            ts.release_gc()
+    (ga, pa, sa), (gb, pb, sb) = res
+    assert torch.equal(ga, gb) and torch.equal(pa, pb)
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+
+
+def test_optimizer_grid_cap_is_bit_identical(dev):
+    """The optimizer sweeps' max_blocks argument (the early sweep's small grid) only decides which workgroup updates which
+    elements: Adam and SGD over the same buffers with the default grid, one workgroup and 256 workgroups give bit-identical
+    parameters and moments (element-wise rules; n not a multiple of 4: Adam's scalar tail included)."""
+    from deeplio_amd import ops
+    gen = torch.Generator().manual_seed(3)
+    n = (1 << 22) + 7
+    p0 = torch.randn(n, generator=gen).to(dev)
+    grads = [torch.randn(n, generator=gen).to(dev) for _ in range(2)]
+    res = []
+    for mb in (0, 1, 256):
+        pa, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
+        ps, buf = p0.clone(), torch.zeros_like(p0)
+        for i, gr in enumerate(grads):
+            ops.adam_step(pa, gr, m, v, 1e-3, 0.9, 0.999, 1e-8, 1e-4, i + 1, max_blocks=mb)
+            ops.sgd_step(ps, gr, buf, 1e-2, 0.9, 1e-4, i + 1, max_blocks=mb)
+        torch.cuda.synchronize()
+        res.append((pa, m, v, ps, buf))
+    assert not torch.equal(res[0][0], p0)
+    for other in res[1:]:
+        for a, b in zip(res[0], other):
+            assert torch.equal(a, b)

@@ -20,10 +20,10 @@ if what in ("prep", "both"):
     ops._PrepCache._refresh_all = refresh
 if what in ("adam", "both"):
     orig_apply = optimizer.Adam._apply
-    def apply(self, lo, hi, count):
+    def apply(self, lo, hi, count, max_blocks=0):
         calls[1] += 1
         if calls[1] <= 6 or lo != 0:         # the early sweep over the tail bucket stays
-            return orig_apply(self, lo, hi, count)
+            return orig_apply(self, lo, hi, count, max_blocks)
     optimizer.Adam._apply = apply
 sys.argv = [os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-isolated", "--steps", "30", "--warmup", "8"]
 runpy.run_path(sys.argv[0], run_name="__main__")

@@ -25,6 +25,7 @@ for (W, B) in ((2048, 8), (256, 2)):
         t = [time.perf_counter()]
         ts._steps += 1
         Fh.lazy_clear()
+        ts._armed = True                  # (as TrainStep.step: the early optimizer sweep from inside backward)
         feats = ts.model.forward_features([[imgs, normals], imus]); t.append(time.perf_counter())
         loss = ts._tail(feats, gf, gg); t.append(time.perf_counter())
         ts.optimizer.zero_grad(); t.append(time.perf_counter())
@@ -33,6 +34,7 @@ for (W, B) in ((2048, 8), (256, 2)):
                 loss.backward()
         else:
             loss.backward()
+        ts._armed = False
         t.append(time.perf_counter())
         ts.optimizer.step(); t.append(time.perf_counter())
         torch.cuda.synchronize(); t.append(time.perf_counter())
